@@ -165,6 +165,62 @@ def _tile_list(e):
     return {"mode": mode, "listed_tile_fraction": round(listed / max(tiles, 1), 4) if mode == 1 and listed >= 0 else None}
 
 
+DUMP_FIELDS = ("xi", "phix", "phiy", "phiz", "lam", "zet")      # Tau3D's six state fields, in download order
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs budget: the whole grid below it, else a fixed sample of cells
+DUMP_SAMPLE_CELLS = 1 << 21     # 6 fields x fp32 x 2^21 cells = 50.3 MB
+DUMP_SEED = 20240917
+
+
+def dump_cells(n):
+    """Flat (z, y, x) indices of the cells --dump-outputs writes for an n^3 grid: every cell when the six fields fit the budget,
+    else a seeded draw (duplicates dropped, ascending) that depends on n alone."""
+    import numpy as np
+    if 6 * 4 * n ** 3 <= DUMP_BYTES:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n ** 3, DUMP_SAMPLE_CELLS, dtype=np.int64))
+
+
+def dump_outputs(outdir, h, n, z0, nzl, clk, world, rank, dist, cdev):
+    """--dump-outputs: what the timed path computed in its last step — the six state fields (the whole grid, or the cells of
+    dump_cells(n)) as float32 and the clock block as float64 scalars — written by rank 0 as outdir/<name>.npy.  At N > 1 every
+    rank contributes the cells of its own planes; the all-reduce sums bit patterns, the other ranks adding zeros."""
+    import numpy as np
+    import torch
+    cells = dump_cells(n)
+    plane = n * n
+    lo, hi = z0 * plane, (z0 + nzl) * plane
+    if cells is None:
+        mine = np.stack(h.download()).reshape(6, -1)
+        out = np.zeros((6, n ** 3), np.float32)
+        out[:, lo:hi] = mine
+    else:
+        out = np.zeros((6, cells.size), np.float32)
+        chunk = max(1, (1 << 24) // plane)       # planes per download: ~400 MB of host memory at 512^2
+        for p0 in range(0, nzl, chunk):
+            p1 = min(nzl, p0 + chunk)
+            a, b = np.searchsorted(cells, [(z0 + p0) * plane, (z0 + p1) * plane])
+            if a == b:
+                continue
+            off = cells[a:b] - (z0 + p0) * plane
+            for i, f in enumerate(h.download_planes(p0, p1)):
+                out[i, a:b] = f.reshape(-1)[off]
+    if world > 1:
+        t = torch.from_numpy(out.view(np.int32)).to(cdev)
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        out = t.cpu().numpy().view(np.float32)
+    if rank != 0:
+        return
+    os.makedirs(outdir, exist_ok=True)
+    shape = (n, n, n) if cells is None else (cells.size,)
+    for i, name in enumerate(DUMP_FIELDS):
+        np.save(os.path.join(outdir, f"{name}.npy"), out[i].reshape(shape))
+    for name in ("t", "d_tau", "dt", "gain", "maxs"):
+        np.save(os.path.join(outdir, f"clock_{name}.npy"), np.float64(getattr(clk, name)))
+    np.save(os.path.join(outdir, "clock_step.npy"), np.float64(clk.step))
+    print(f"bench.py: wrote {len(DUMP_FIELDS)} fields ({'all' if cells is None else cells.size} cells of {n}^3) and the clock "
+          f"to {outdir}", file=sys.stderr)
+
+
 def _event_timed(torch, stream, enqueue, sync):
     """ms of `enqueue()` on `stream`, from events recorded ON that stream (the handles launch on it)"""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -348,10 +404,16 @@ def main():
                          "those planes byte for byte (ring.matches_single_domain; a mismatch exits 4)")
     ap.add_argument("--ring-driver", choices=("c", "python"), default="c",
                     help="c: the library's ring (tau3d_ring_*, librccl called from C); python: fluid-sims_amd/slab.py over torch.distributed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed as DIR/<name>.npy: the six fields (float32; the whole "
+                         "grid up to 64 MB, else the same seeded sample of 2^21 cells for every run at this --grid) and the clock "
+                         "block (float64).  The inputs depend on the arguments alone, so two builds can be compared file for file")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_self_spawn(args.gpus))
 
@@ -594,6 +656,8 @@ def main():
     frange = h.field_range()
     utiles = h.uniform_tiles()
     tlist = _tile_list(h)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, n, z0, nzl, clk, world, rank, dist if world > 1 else None, "cpu" if shared else dev)
 
     # ---- the ring run proves itself: slab == single domain, byte for byte (SURVEY 8e's parity oracle, on the hardware and with
     # the transport that was just timed).  The grid fits one GPU, so EVERY rank recomputes warmup + steps single-domain steps from

@@ -1,6 +1,6 @@
 #!/bin/bash
 # ISA summary of one h3d kernel's march loop: usage scripts/k2_isa.sh [mangled-name-prefix]
-cd /root/repo/fluid-sims_amd && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize $H3D_DEFS -S --cuda-device-only csrc/h3d.hip -o /tmp/h3d.s 2>&1 | grep -E "error" ; cd /root/repo
+cd "$(dirname "$0")/.." && (cd fluid-sims_amd && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize $H3D_DEFS -S --cuda-device-only csrc/h3d.hip -o /tmp/h3d.s 2>&1 | grep -E "error")
 python - "$@" <<'PY'
 import re,sys
 sys.path.insert(0,'scripts')

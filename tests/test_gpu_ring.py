@@ -47,7 +47,8 @@ def test_tau3d_host_ring_is_bit_identical(eng, tmp_path, shape, frames, transpor
     grid = ["--nx", str(nx), "--ny", str(ny), "--nz", str(nz), "--frames", str(frames), "--start", "1"]
     want, _ = dump_of(tmp_path, "single.bin", *grid)
     assert len(want) > 6 * 4 * nx * ny * nz
-    for world in (2, 3, 4, 8):
+    # at most 5 ranks: with this test process they are the 6 processes that may hold the one shared device at once
+    for world in (2, 3, 4, 5):
         if nz // world < 6:
             continue
         got, out = dump_of(tmp_path, f"w{world}.bin", *grid, "--gpus", str(world), "--transport", transport)
@@ -252,7 +253,8 @@ def test_bench_two_ranks_end_to_end_on_one_gpu(eng, transport, word):
     assert [r["rank"] for r in pr] == [0, 1] and all(r["xy_ms"] > 0 and r["z_ms"] > 0 and r["exchange_ms"] > 0 and r["allreduce_ms"] > 0 for r in pr), pr
 
 
-@pytest.mark.parametrize("ranks,grid", [(2, 128), (8, 128)])
+# 4 ranks at most: this test process, the launcher and the ranks stay within the 6 processes that may hold the shared device
+@pytest.mark.parametrize("ranks,grid", [(2, 128), (4, 128)])
 def test_bench_auto_transport_probe_on_one_gpu(eng, ranks, grid):
     """`bench.py --gpus N` with the default --ring-transport auto, the command the driver's scaling run issues: both candidate
     transports are built, timed over a few warm-up steps and closed again, the faster one is rebuilt for the timed region, and

@@ -38,7 +38,8 @@ def test_tgs_row_ring_is_bit_identical(eng, tmp_path, nx, ny, steps):
     grid = ["--nx", str(nx), "--ny", str(ny), "--steps", str(steps)]
     want, out1 = dump_of(tmp_path, "single.bin", *grid)
     assert len(want) > 2 * 4 * nx * ny
-    for world, halo in ((2, 4), (3, 4), (4, 8), (8, 4), (2, 1)):
+    # at most 5 ranks: with this test process they are the 6 processes that may hold the one shared device at once
+    for world, halo in ((2, 4), (3, 4), (4, 8), (5, 4), (2, 1)):
         if ny // world < halo:
             continue
         got, out = dump_of(tmp_path, f"w{world}h{halo}.bin", *grid, "--gpus", str(world), "--transport", "host", "--halo", str(halo))

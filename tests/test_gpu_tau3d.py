@@ -373,7 +373,7 @@ def test_create_upload_step_without_init(eng, shape):
     b.close()
 
 
-def test_split_step_equals_fused_step_to_rounding(eng):
+def test_split_step_equals_fused_step_to_rounding(eng, tmp_path):
     """The two-kernel step (k_flux_xy + k_update_z over the primitive cache, cell-centred WENO on every axis) and the
     fused k_step (face-centred WENO on x / y) are different groupings of the same arithmetic: one step from the same
     state agrees far inside the 1e-5 contract in the well-conditioned fields."""
@@ -391,7 +391,7 @@ np.save(sys.argv[1], np.stack(e.download()))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = {}
     for split in ("0", "1"):
-        path = os.path.join("/tmp", f"tau3d_split{split}.npy")
+        path = str(tmp_path / f"tau3d_split{split}.npy")
         env = dict(os.environ, TAU3D_SPLIT=split)
         subprocess.run([sys.executable, "-c", code, path], check=True, cwd=root, env=env)
         out[split] = np.load(path)
@@ -401,7 +401,7 @@ np.save(sys.argv[1], np.stack(e.download()))
         assert r[k] <= 2e-5, (k, r[k])          # 12 steps of accumulated rounding between two legal groupings
 
 
-def test_split_step_is_the_same_for_every_chunk_length():
+def test_split_step_is_the_same_for_every_chunk_length(tmp_path):
     """k_update_z's chunk length (TAU3D_ZCHUNK planes per workgroup) only decides which workgroup computes a plane: every
     chunk addresses its planes as 32-bit offsets from its own first plane and primes its own ring, so the state after
     several steps must not change by a bit — odd lengths, a length that does not divide nz, one chunk for everything."""
@@ -419,7 +419,7 @@ np.save(sys.argv[1], np.stack(e.download()))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
     for zc in ("0", "1", "7", "16", "40"):
-        path = os.path.join("/tmp", f"tau3d_zc{zc}.npy")
+        path = str(tmp_path / f"tau3d_zc{zc}.npy")
         env = dict(os.environ, TAU3D_SPLIT="1", TAU3D_ZCHUNK=zc)
         subprocess.run([sys.executable, "-c", code, path], check=True, cwd=root, env=env)
         outs.append(np.load(path))
