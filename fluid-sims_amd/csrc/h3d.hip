@@ -94,6 +94,9 @@ struct DevClock {
 static_assert(offsetof(DevClock, maxs_bits) % 32 == 0 && offsetof(DevClock, fmax_bits) == offsetof(DevClock, maxs_bits) + 4,
               "tau3d_max_ptr hands out {maxs_bits, fmax_bits} as one aligned 2-word tensor");
 
+// dzero words: bit 0 the tile's divergence is zero, bit 1 k_tile_predict's prediction, bits 2-7 (DZ_HELD0 << m) the output buffer
+// holds field m of the predicted state already (k_tile_predict)
+constexpr unsigned DZ_HELD0 = 4u, DZ_HELD_ALL = 0xFCu;
 // kernel arguments (by value -> SGPRs)
 constexpr unsigned UF_ALL = 1u, UF_W = 2u, UF_E = 4u, UF_S = 8u, UF_N = 16u, UF_PRED = 32u;
 constexpr int UREC = 24, USTRIP = 6;   // floats per tile record; width of an edge strip = the reach of two steps' stencils (2 x HALO)
@@ -125,7 +128,7 @@ struct Args {
   unsigned *ucount_host;                  // k_flux_xy_list: the length again, in mapped host memory (the host sizes later launches by it)
   unsigned list_grid; int list_fast;      // k_flux_xy_list_rest: the main launch's grid and weight form
   int z_fill;                             // k_update_z: 0, or k_fill_z follows and takes the fully predicted chunks (1: if the fast weight form is due, 2: the other)
-  int z_pred;                             // k_update_z: bits 1 / 2 of a dzero word are this step's prediction (k_tile_predict ran before it) —
+  int z_pred;                             // k_update_z: bits 1-7 of a dzero word are this step's prediction (k_tile_predict ran before it) —
                                           // 0: no, 1: yes but every plane is marched all the same (TAU3D_Z_SKIP=0), 2: predicted planes store the record's state
   int pred_commit;                        // 0: the verifying mode — flags into a scratch pair, the next k_flux_xy still runs every tile
   // the same groups as one base + stride (field m at base + m * stride): what k_update_z addresses them through
@@ -1708,17 +1711,21 @@ template <bool FAST, int PART = 0> __device__ __forceinline__ void update_z_body
   const bool uex = A.dzero != nullptr;
   const bool zsk = uex && A.z_pred == 2;
   // The chunk's prediction bits for the wave's two tiles (see "Predicted-uniform tiles" below): lane l reads the words of plane zc_lo + l.
+  // held (k_fill_z): lane l keeps both tiles' "the buffer holds field m" bits of that plane (first tile in bits 0-5, second in 6-11).
   unsigned long long pmask = 0ull, smask = 0ull;
+  unsigned held = 0u;
   if (zsk) {
     const int xa = bx * ZT_X, xb = xa + XT;              // the wave's two tiles start here (ZT_X = 2 XT)
     const int zl = zc_lo + lx;                           // this lane's plane of the chunk
     unsigned both = 0u;
     if (zl < zc_hi && xb + XT <= A.nx && y < A.ny) {
       const unsigned *const w = A.dzero + ((size_t)zl * A.dz_nty + (size_t)(y / YT)) * A.dz_ntx + (size_t)(xa / XT);
-      both = w[0] & w[1];
+      const unsigned w0 = w[0], w1 = w[1];
+      both = w0 & w1;
+      if (PART == 2) held = ((w0 & DZ_HELD_ALL) >> 2) | ((w1 & DZ_HELD_ALL) << 4);
     }
     pmask = __builtin_amdgcn_ballot_w64((both & 2u) != 0u);
-    smask = __builtin_amdgcn_ballot_w64((both & 4u) != 0u);
+    smask = __builtin_amdgcn_ballot_w64((both & DZ_HELD_ALL) == DZ_HELD_ALL);
   }
   // A chunk ALL of whose planes are predicted for both tiles of the wave (most chunks away from the disturbance): every cell of it
   // holds the state S of its tile's record, and the march below would compute update_cell(S, +0, F, F) at its first plane and store
@@ -1742,10 +1749,19 @@ template <bool FAST, int PART = 0> __device__ __forceinline__ void update_z_body
       for (int m = 0; m < 6; m++) E[m] = er[m];
       GChar *const outB = (GChar *)(A.out0 + (size_t)(zc_lo + HALO) * plane_n);
       unsigned vo = col4;
+      const int hs = lx < XT ? 0 : 6;   // this lane's tile among the two of the wave: its half of the held bits
       for (int z = zc_lo; z < zc_hi; z++) {
         size_t f4 = fs4;
         asm volatile("" : "+s"(f4));
-        if ((smask & 1ull) == 0ull) {   // (steady: the buffer holds these bits already)
+        if (PART == 2) {
+          // field by field, each store behind its own tile's bit: a field the buffer holds already (k_tile_predict) is not stored,
+          // and one that neither tile of the wave stores costs no store instruction
+          const unsigned hz = (unsigned)__builtin_amdgcn_readlane((int)held, z - zc_lo) >> hs;
+          const unsigned vb = lane_off(vo);
+#pragma unroll
+          for (int m = 0; m < 6; m++)
+            if (((hz >> m) & 1u) == 0u) gst(outB + m * f4, vb, E[m]);
+        } else if ((smask & 1ull) == 0ull) {   // (PART 0, never taken at run time: fullp implies k_fill_z's launch)
           const unsigned vb = lane_off(vo);
 #pragma unroll
           for (int m = 0; m < 6; m++) gst(outB + m * f4, vb, E[m]);
@@ -1852,9 +1868,8 @@ template <bool FAST, int PART = 0> __device__ __forceinline__ void update_z_body
   // full ones do).
   float memoE[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   bool memo = false;
-  // Steady tiles (bit 2, see k_tile_predict): where the new state of a predicted plane is, bit for bit, the state the plane holds
-  // now AND held a step ago, the output buffer — the input of the step before — holds it already: no store (smask: the planes where
-  // both tiles of the wave are steady).
+  // Steady planes (bits 2-7, see k_tile_predict): where the output buffer — the input of the step before — holds all six fields of
+  // the new state of a predicted plane already, in both tiles of the wave, nothing is stored (smask; k_fill_z goes field by field).
 
   for (int z = zc_lo; z < zc_hi; z++) {
     const bool more = z + 1 < zc_hi;
@@ -2227,9 +2242,14 @@ __global__ __launch_bounds__(PREDICT_NT) void k_tile_predict(const Args A) {
   // The NEW state of a predicted tile, once per tile: update_cell on S with the flagged +0 divergence and a z flux difference of
   // F - F — what k_update_z computes in every cell of it (the difference is +-0 there and meets +0: the same -(+0)).  It goes into
   // the tile's record for the next step (what k_flux_xy's test would take as its reference) and k_update_z / k_fill_z store it in the
-  // cells.  Steady tiles: predicted now AND by the step before (its flag carries UF_PRED: not a k_flux_xy's), the state then (the
-  // record this one replaces) = the state now = the new state, bit for bit: the buffer k_update_z is about to write is the input of
-  // step n - 1 and holds those bits in every cell of the tile — no store (bit 2 of the dzero word).
+  // cells.
+  // Fields the buffer already holds (bits 2-7 of the dzero word, bit 2 + m for field m).  A.uflag_r / A.uref_r describe this step's
+  // input, state n; A.pref is the record of state n - 1, which this kernel overwrites with state n + 1.  If the tile's flag for state
+  // n carries UF_PRED, the step before predicted it — from a state n - 1 uniform in the tile, whose record is pr.  The buffer
+  // k_update_z / k_fill_z write now is the input of that step (whatever writes the state outside a step drops the list, and the
+  // next k_flux_xy writes flags without UF_PRED), so every cell of the tile's planes there holds pr, bit for bit.  Field m may then
+  // skip its store where bits(pr[m]) == bits(E[m]): that needs nothing about the other five fields and nothing about state n (a
+  // field that settles on a two-cycle skips too).  pred_commit: in the verifying mode the flags are a scratch pair, not this.
   {
     float smax = 0.f, fmx = 0.f;
     if (ok) {
@@ -2243,15 +2263,16 @@ __global__ __launch_bounds__(PREDICT_NT) void k_tile_predict(const Args A) {
       for (int m = 0; m < 6; m++) own[m] = ZDEC(A.u_ref, m, S6[m]);
       const int xt = (int)(t % (unsigned)ntx) * XT;   // (any column of the tile: none of them is in a sponge zone)
       update_cell(A, K, own, Z6, Z6, Z6, A.clk->dt, A.inv_dz, A.clk->gain, xt, E, smax, fmx);
-      bool steady = A.pred_commit && (A.uflag_r[t] & UF_PRED) != 0u;
+      const bool was_pred = A.pred_commit && (A.uflag_r[t] & UF_PRED) != 0u;
       float *const pr = A.pref + (size_t)t * UREC;
+      unsigned held = 0u;
 #pragma unroll
       for (int m = 0; m < 6; m++) {
-        steady = steady && __float_as_uint(pr[m]) == __float_as_uint(S6[m]) && __float_as_uint(E[m]) == __float_as_uint(S6[m]);
+        held |= (was_pred && __float_as_uint(pr[m]) == __float_as_uint(E[m])) ? DZ_HELD0 << m : 0u;
         pr[m] = E[m];
       }
       A.pflag[t] = UF_ALL | UF_PRED;
-      A.dzero[t] = steady ? 7u : 3u;   // bit 1: k_update_z's copy of the prediction (a k_flux_xy that runs the tile writes 0 or 1)
+      A.dzero[t] = 3u | held;   // bit 1: k_update_z's copy of the prediction (a k_flux_xy that runs the tile writes 0 or 1)
     } else if (valid) {
       A.pflag[t] = 0u;
       A.dzero[t] = A.dzero[t] & 1u;
@@ -2293,6 +2314,31 @@ __global__ __launch_bounds__(256) void k_tile_predict_check(const unsigned *pfla
   bool same = (uflag[t] & UF_ALL) != 0u;
   for (int m = 0; m < 6 && same; m++) same = __float_as_uint(pref[(size_t)t * UREC + m]) == __float_as_uint(uref[(size_t)t * UREC + m]);
   if (!same) atomicAdd(bad, 1u);
+}
+
+// tau3d_store_skip_stats: over the dzero words of the last step, the cells of predicted tiles (c[6]) and those of them whose buffer
+// held field m already (c[m]: k_fill_z skipped the store; k_update_z's march only where all six fields of both tiles of a wave did)
+__global__ __launch_bounds__(256) void k_store_skip_stats(const unsigned *dzero, int nx, int ny, int ntx, int nty, unsigned nt,
+                                                          unsigned long long *c) {
+  const unsigned t = blockIdx.x * 256u + threadIdx.x;
+  unsigned long long v[7] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+  if (t < nt) {
+    const unsigned w = dzero[t];
+    const int bx = (int)(t % (unsigned)ntx), by = (int)((t / (unsigned)ntx) % (unsigned)nty);
+    const unsigned long long cells = (unsigned long long)(min(XT, nx - bx * XT) * min(YT, ny - by * YT));
+    if (w & 2u) {
+      v[6] = cells;
+#pragma unroll
+      for (int m = 0; m < 6; m++) v[m] = (w & (DZ_HELD0 << m)) ? cells : 0ull;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    unsigned long long x = v[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    if (__lane_id() == 0 && x != 0ull) atomicAdd(&c[k], x);
+  }
 }
 
 struct InitVals { float f[6]; float s[6]; }; // encoded fluid / solid cell values (host-computed, libm)
@@ -3043,6 +3089,7 @@ static int step_ranges(tau3d_t *h, int zl_lo, int zl_hi, int zl_lo2, int zl_hi2,
     }
     return 0;
   }
+  h->list_ok = false;   // (the fused kernel writes no tile flags: a later split step must not trust the ones it finds)
   // Planes marched by one workgroup.  Large grids: enough workgroups (~32k) to load-balance 256 CUs x 3 resident
   // groups, chunks of 8..32 planes (a chunk re-decodes 4 warm-up planes, so longer is cheaper).  Small grids are
   // LATENCY bound instead — a 64^3 launch is 128 workgroups of 13 serial plane iterations with chunks of 8 — so
@@ -3388,6 +3435,33 @@ extern "C" int tau3d_tile_list_stats(tau3d_t *h, int *mode, long *listed, long *
   if (mismatches) *mismatches = (long)c[2];
   return 0;
 }
+/* the predicted tiles of the LAST step (dzero bit 1): *predicted_cells their cells, counts[m] those whose output buffer already held
+ * field m of the new state (k_tile_predict's bits 2-7), so that k_fill_z skipped its store (include/taueng.h: the march's rule).  Zero without a tile list.  Computed on
+ * demand by a small kernel over the tile words; waits for the stream. */
+extern "C" int tau3d_store_skip_stats(tau3d_t *h, long counts[6], long *predicted_cells) {
+  if (!h) return tau::fail("tau3d_store_skip_stats: null handle");
+  TAU_HIP(hipSetDevice(h->device));
+  unsigned long long c[7] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+  if (h->split && h->uniform_exits && h->dzero && h->uflag[0] != nullptr) {
+    const int ntx = (h->p.nx + h3d::XY_FX - 1) / h3d::XY_FX, nty = (h->p.ny + h3d::XY_FY - 1) / h3d::XY_FY;
+    const unsigned nt = (unsigned)((size_t)ntx * nty * (size_t)h->nzl);
+    unsigned long long *d = nullptr;
+    TAU_HIP(hipMalloc(&d, sizeof(c)));
+    hipError_t e = hipMemsetAsync(d, 0, sizeof(c), h->stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(h3d::k_store_skip_stats, dim3((nt + 255u) / 256u), dim3(256), 0, h->stream, (const unsigned *)h->dzero,
+                         h->p.nx, h->p.ny, ntx, nty, nt, d);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(c, d, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    hipFree(d);
+    if (e != hipSuccess) return tau::fail("tau3d_store_skip_stats: %s", hipGetErrorString(e));
+  }
+  for (int m = 0; m < 6; m++) if (counts) counts[m] = (long)c[m];
+  if (predicted_cells) *predicted_cells = (long)c[6];
+  return 0;
+}
 extern "C" int tau3d_slab_info(tau3d_t *h, int *z0, int *nzl, int *nz, int *device, void **stream) {
   if (!h) return tau::fail("tau3d_slab_info: null handle");
   if (z0) *z0 = h->z0;
@@ -3448,6 +3522,7 @@ extern "C" int tau3d_set_split(tau3d_t *h, int on) {
     return build_solid(h);   // fills the tile flags (the mask itself is rebuilt identically)
   }
   h->split = on != 0;
+  h->list_ok = false;   // (the flags describe the state the last split step made; a switch either way drops them)
   return 0;
 }
 extern "C" int tau3d_max_ptr(tau3d_t *h, float **p) {

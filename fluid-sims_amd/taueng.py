@@ -150,6 +150,7 @@ def load():
         "tau3d_field_range": ([vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(i32)], i32),
         "tau3d_uniform_tiles": ([vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(i32)], i32),
         "tau3d_tile_list_stats": ([vp, C.POINTER(i32), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_long)], i32),
+        "tau3d_store_skip_stats": ([vp, C.POINTER(C.c_long), C.POINTER(C.c_long)], i32),
         "tau3d_sync": ([vp], i32),
         "tau_device_count": ([C.POINTER(i32)], i32),
         "tau_guided_chunks": ([i32, i32, i32, i32, i32, C.POINTER(i32), i32, C.POINTER(i32)], i32),
@@ -545,6 +546,13 @@ class Tau3D:
         m, l, n, c, b = C.c_int(), C.c_long(), C.c_long(), C.c_long(), C.c_long()
         _ck(self._L.tau3d_tile_list_stats(self._h, C.byref(m), C.byref(l), C.byref(n), C.byref(c), C.byref(b)))
         return m.value, l.value, n.value, c.value, b.value
+
+    def store_skip_stats(self):
+        """(counts[6], predicted_cells) — tau3d_store_skip_stats: of the last step's predicted cells, those whose store of field m was
+        skipped (the output buffer held the field already)"""
+        c, p = (C.c_long * 6)(), C.c_long()
+        _ck(self._L.tau3d_store_skip_stats(self._h, c, C.byref(p)))
+        return list(c), p.value
 
     def field_range(self):
         """(read_max, written_max, fast_form) — see tau3d_field_range"""

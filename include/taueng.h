@@ -180,6 +180,10 @@ int tau3d_uniform_tiles(tau3d_t *h, long *uniform, long *tiles, int *enabled);
  * tile).  mode: what this handle does (0 also for ragged tiles; a slab predicts no plane within three of its edges); listed: length of the list made by the last step (-1: none
  * valid); checked / mismatches: mode 2's tally (mismatches must stay 0).  Waits for the stream.  Same bits in every mode. */
 int tau3d_tile_list_stats(tau3d_t *h, int *mode, long *listed, long *tiles, long *checked, long *mismatches);
+/* the last step's predicted tiles: *predicted_cells their cells, counts[m] those whose output buffer already held field m, so that the
+ * store was skipped (k_fill_z, field by field; the z march of a partly predicted chunk skips a plane only where all six were held in
+ * both tiles of a wave).  Zeros without a tile list.  Computed on demand by a small kernel; waits for the stream. */
+int tau3d_store_skip_stats(tau3d_t *h, long counts[6], long *predicted_cells);
 /* The pointers of tau3d_state_ptrs are for reading.  A caller that does write the state (or the solid mask) through them
  * says so here before the next step (tau3d_init / tau3d_upload_* do it themselves): the field range is measured again and
  * the static solid-free tile flags of the x/y flux kernel are rebuilt from the mask. */
