@@ -56,7 +56,7 @@ struct Args {
   float visc_nu, visc_rho, visc_e;
   float in_r, in_u, in_p;  // inflow_state(), :230-238
   C4 in_c;
-  int uniform_exits;       // k_march_lds: trips whose five-row window holds one state skip the predictors and the faces (TAUH2_UNIFORM_EXITS=0: off)
+  unsigned long long *trips;   // k_march_lds<1, true>: null, or [0] += the trips that took the uniform-region exit, [1] += all trips (tauh2_uniform_trips)
 };
 
 __device__ __forceinline__ float vreg(float s) {   // a wave-uniform value moved into a VGPR
@@ -709,6 +709,7 @@ __global__ __launch_bounds__(64 * WPB, TAU_H2_LDS_WAVES) void k_march_lds(const 
   // recomputed from that one state when the stretch ends (`stale`): the same calls on the same operands.
   int ucnt = 0;
   bool stale = false;
+  int nuni = 0;   // trips of this wave that took the exit (wave-uniform: counted only where A.trips is set, one atomic at the end)
   float ur0 = 0.f, ur1 = 0.f, ur2 = 0.f, ur3 = 0.f;
   for (int a = j0; a <= j1 + 1; a++) {
     { const int t = s0; s0 = s1; s1 = s2; s2 = s3; s3 = s4; s4 = t; }   // window = rows a-4 .. a in slots s0 .. s4
@@ -759,6 +760,7 @@ __global__ __launch_bounds__(64 * WPB, TAU_H2_LDS_WAVES) void k_march_lds(const 
       // nothing to evaluate: dFx of row a-2 is +0 (one x flux in every lane), Gy - Gy_lo is +0 (one y flux either side of row a-2)
       dFx = C4{0.f, 0.f, 0.f, 0.f}; Gy_lo = C4{0.f, 0.f, 0.f, 0.f};
       stale = true;
+      nuni++;
     } else {
     if (UEX && stale) {   // the stretch has ended: rows a-4 .. a-1 still hold its state; what the last (skipped) trip would have left behind
       P4 lo_u, hi_u;
@@ -839,6 +841,10 @@ __global__ __launch_bounds__(64 * WPB, TAU_H2_LDS_WAVES) void k_march_lds(const 
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) smax = fmaxf(smax, __shfl_xor(smax, o, 64));
   if (lane == 0) tau::atomic_max_float_bits(&A.st->maxs_bits[(A.slot + 1) % 3], smax);
+  if (UEX && A.trips && lane == 0) {
+    atomicAdd(&A.trips[0], (unsigned long long)nuni);
+    atomicAdd(&A.trips[1], (unsigned long long)(j1 + 2 - j0));   // the loop's trips: a = j0 .. j1 + 1
+  }
 }
 
 // max wavespeed of a freshly initialised / uploaded state (the reference's two reduction kernels)
@@ -990,6 +996,9 @@ struct tauh2 {
   int *crow = nullptr;      // chunk schedule of the march (h2_schedule)
   int crow_n = 0;
   bool uniform_exits = true;   // TAUH2_UNIFORM_EXITS=0 at tauh2_create: every trip of the march evaluates its predictors and faces (same bits)
+  unsigned long long *trips = nullptr;   // tauh2_uniform_trips: the last step's [skipped, all] trips of k_march_lds<1, true> (null: not counting)
+  bool trips_on = false;
+  bool uex_ran = false;                  // the last step launched k_march_lds<1, true> (the kernel with the exits)
 };
 
 namespace {
@@ -1083,7 +1092,7 @@ extern "C" void tauh2_destroy(tauh2_t *h) {
   for (int s = 0; s < 2; s++)
     for (int f = 0; f < 4; f++) hipFree(h->buf[s][f]);
   hipFree(h->mask); hipFree(h->st);
-  hipFree(h->rval); hipFree(h->rpix); hipFree(h->rmm); hipFree(h->crow);
+  hipFree(h->rval); hipFree(h->rpix); hipFree(h->rmm); hipFree(h->crow); hipFree(h->trips);
   if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1155,7 +1164,8 @@ static int h2_launch_step(tauh2 *h, float dt_explicit) {
   for (int f = 0; f < 4; f++) { A.in[f] = h->buf[h->cur][f]; A.out[f] = h->buf[h->cur ^ 1][f]; }
   A.slot = h->slot; A.dt_explicit = dt_explicit;
   const bool uexits = h->uniform_exits;
-  A.uniform_exits = uexits ? 1 : 0;
+  A.trips = nullptr;
+  h->uex_ran = false;
   if (!h->maxs_valid) { // first step after init / upload: one reduction pass
     TAU_HIP(hipMemsetAsync(h->st->maxs_bits, 0, sizeof(h->st->maxs_bits), h->stream));
     hipLaunchKernelGGL(h2d::k_maxspeed, dim3(2048), dim3(256), 0, h->stream, A);
@@ -1184,6 +1194,11 @@ static int h2_launch_step(tauh2 *h, float dt_explicit) {
     const int *crow = nullptr;
     if (lds_win && rows_env < 1 && h2_schedule(h, &nchunks, &crow)) return 1;
     const unsigned nwork = (unsigned)(nstrips * nchunks);
+    if (lds_win && wpb == 1 && uexits && h->trips_on) {   // counting: the same kernel, told where to add its trips
+      TAU_HIP(hipMemsetAsync(h->trips, 0, 2 * sizeof(unsigned long long), h->stream));
+      A.trips = h->trips;
+    }
+    h->uex_ran = lds_win && wpb == 1 && uexits;
     if (lds_win && wpb == 1 && uexits) hipLaunchKernelGGL((h2d::k_march_lds<1, true>), dim3(nwork), dim3(64), 0, h->stream, A, rows, nstrips, nchunks, crow);
     else if (lds_win && wpb == 1) hipLaunchKernelGGL((h2d::k_march_lds<1, false>), dim3(nwork), dim3(64), 0, h->stream, A, rows, nstrips, nchunks, crow);
     else if (lds_win && wpb == 2) hipLaunchKernelGGL((h2d::k_march_lds<2, false>), dim3((nwork + 1) / 2), dim3(128), 0, h->stream, A, rows, nstrips, nchunks, crow);
@@ -1202,6 +1217,25 @@ extern "C" int tauh2_step_async(tauh2_t *h, int nsteps) {
   TAU_HIP(hipSetDevice(h->device));
   for (int s = 0; s < nsteps; s++)
     if (h2_launch_step(h, 0.f)) return 1;
+  return 0;
+}
+/* counting of the uniform-region exits (on = 1 from the next step, 0 off); the last step's counts: see include/taueng.h */
+extern "C" int tauh2_uniform_trips(tauh2_t *h, int on, long *skipped, long *trips, int *enabled) {
+  if (!h) return tau::fail("tauh2_uniform_trips: null handle");
+  TAU_HIP(hipSetDevice(h->device));
+  unsigned long long c[2] = {0ull, 0ull};
+  if (h->trips_on && h->uex_ran) {
+    TAU_HIP(hipMemcpyAsync(c, h->trips, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+    TAU_HIP(hipStreamSynchronize(h->stream));
+  }
+  if (skipped) *skipped = (long)c[0];
+  if (trips) *trips = (long)c[1];
+  if (enabled) *enabled = h->uex_ran ? 1 : 0;
+  if (on && !h->trips) {
+    TAU_HIP(hipMalloc(&h->trips, 2 * sizeof(unsigned long long)));
+    TAU_HIP(hipMemsetAsync(h->trips, 0, 2 * sizeof(unsigned long long), h->stream));
+  }
+  h->trips_on = on != 0;
   return 0;
 }
 extern "C" int tauh2_sync(tauh2_t *h) {

@@ -101,6 +101,27 @@ def _load_hip_runtime():
     raise TauError(f"no HIP runtime (libamdhip64) could be loaded: {err}")
 
 
+_HIP = None
+
+
+def _hip_runtime():
+    """the HIP runtime the engine is bound to, with the signatures of the few calls made from Python"""
+    global _HIP
+    if _HIP is None:
+        h = _load_hip_runtime()
+        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        h.hipMemcpy.restype = C.c_int
+        h.hipDeviceSynchronize.argtypes = []
+        h.hipDeviceSynchronize.restype = C.c_int
+        _HIP = h
+    return _HIP
+
+
+def _ck_hip(err, what):
+    if err != 0:
+        raise TauError(f"{what}: hipError {err}")
+
+
 def load():
     """Load libtaueng.so (raises TauError when it has not been built)."""
     global _lib
@@ -188,6 +209,7 @@ def load():
         "tauh2_step_explicit": ([vp, C.c_double], i32),
         "tauh2_get_time": ([vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)], i32),
         "tauh2_sync": ([vp], i32),
+        "tauh2_uniform_trips": ([vp, i32, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(i32)], i32),
         "tauh2_unit_eval": ([vp, C.POINTER(f32)], i32),
         "tauh2_unit_neighbors": ([vp, i32, i32, C.POINTER(f32)], i32),
         "tauh2_body_sdf": ([C.c_double] * 5, C.c_double),
@@ -528,6 +550,22 @@ class Tau3D:
         _ck(self._L.tau3d_palette_indices(self._h, gamma, out.ctypes.data_as(C.c_void_p), C.byref(mn), C.byref(mx)))
         return out, mn.value, mx.value
 
+    def state_ptrs(self):
+        """device addresses of the current state's six fields (nzl x ny x nx each, no halo) and of the solid mask (uint8, same
+        layout) — tau3d_state_ptrs.  The field pointers change with every step.  After writing through them: state_written()."""
+        ptrs, sol = (C.c_void_p * 6)(), C.c_void_p()
+        _ck(self._L.tau3d_state_ptrs(self._h, ptrs, C.byref(sol)))
+        return [p for p in ptrs], sol.value
+
+    def write_device(self, dptr, arr, offset=0):
+        """copy host array `arr` to device address dptr + offset bytes (a pointer of state_ptrs): waits for the handle's stream
+        first and for the copy after — then call state_written()"""
+        a = np.ascontiguousarray(arr)
+        self.sync()
+        H = _hip_runtime()
+        _ck_hip(H.hipMemcpy(C.c_void_p(dptr + offset), a.ctypes.data_as(C.c_void_p), a.nbytes, 1), "hipMemcpy (host to device)")
+        _ck_hip(H.hipDeviceSynchronize(), "hipDeviceSynchronize")
+
     def state_written(self):
         _ck(self._L.tau3d_state_written(self._h))
 
@@ -695,6 +733,12 @@ class Hypersonic2D:
 
     def sync(self):
         _ck(self._L.tauh2_sync(self._h))
+
+    def uniform_trips(self, on=True):
+        """(skipped, trips, enabled) of the last step — tauh2_uniform_trips; counting is on from the next step if `on`"""
+        s, n, en = C.c_long(), C.c_long(), C.c_int()
+        _ck(self._L.tauh2_uniform_trips(self._h, 1 if on else 0, C.byref(s), C.byref(n), C.byref(en)))
+        return s.value, n.value, bool(en.value)
 
 
 class Sph2D:

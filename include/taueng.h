@@ -305,6 +305,12 @@ int tauh2_unit_neighbors(tauh2_t *h, int x, int y, float out[9]);
 double tauh2_body_sdf(double x, double y, double Rb, double Rn, double theta); /* sdSphereConeCapsule, :644-686 */
 int tauh2_get_time(tauh2_t *h, double *t, double *dt_last, double *maxs, int *step);
 int tauh2_sync(tauh2_t *h);
+/* Counting of the march's uniform-region exits (h2d::k_march_lds<1, true>: a trip whose five-row window holds one state skips the
+ * predictors and faces).  on = 1 counts from the next step on (0: off, the kernel is told nothing); reports the LAST step: *skipped
+ * its trips that took the exit, *trips all trips of the march (zeros when not counting), *enabled 1 if that step ran the kernel with
+ * the exits — 0 for the small-grid tile kernel, the register-window march, TAUH2_UNIFORM_EXITS=0 and TAU_H2_WPB != 1.  The counted
+ * kernel is the one that ships: a pointer in its arguments, one atomic per wave.  Waits for the stream.  Any out pointer may be NULL. */
+int tauh2_uniform_trips(tauh2_t *h, int on, long *skipped, long *trips, int *enabled);
 
 /* =====================================================================
  * 2D WCSPH — replaces the per-sub-step launches of tau_sph.cu:676-701 (clear heads, build

@@ -6,7 +6,6 @@ the state is copied device to device into torch tensors, nothing is downloaded),
 output buffer already held the field (tau3d_store_skip_stats: k_tile_predict's per-field bits, the stores k_fill_z skips).
 Two windows: the headline start (impulsive start, clock (0.02, 1e-4), steps 5-25) and the late state (ramped start + --late steps)."""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -15,27 +14,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import fluid_sims_amd as f  # noqa: E402
-
-FIELDS = ("xi", "phix", "phiy", "phiz", "lam", "zet")
-
-
-def hip():
-    from fluid_sims_amd import taueng
-    h = taueng._load_hip_runtime()
-    h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    h.hipMemcpy.restype = C.c_int
-    return h
-
-
-def snapshot(e, H, dst):
-    """the handle's current state into dst (int32, (6, nz, ny, nx)), device to device"""
-    ptrs, sol = (C.c_void_p * 6)(), C.c_void_p()
-    e.sync()
-    assert e._L.tau3d_state_ptrs(e._h, ptrs, C.byref(sol)) == 0
-    nb = dst[0].numel() * 4
-    for m in range(6):
-        assert H.hipMemcpy(dst[m].data_ptr(), ptrs[m], nb, 3) == 0   # hipMemcpyDeviceToDevice
-    torch.cuda.synchronize()
+from tests.devstate import FIELDS, hip, snapshot  # noqa: E402,F401
 
 
 def window(e, H, steps, label):

@@ -216,20 +216,32 @@ def test_uniform_row_exits_change_no_bit(eng, tmp_path, W, H, steps):
     ahead of and beside the bow shock: almost every trip of the BASELINE input's first hundreds of steps) and recomputes what the
     skipped trips would have handed on when the stretch ends.  TAUH2_UNIFORM_EXITS=0 evaluates everything: every field of every cell
     and the clock must be byte-identical, on grids that run the march by default, early (mostly free stream) and late (shock layer
-    grown) in a run."""
+    grown) in a run.  The last step's trips are counted (tauh2_uniform_trips): with the exits on, the kernel that has them ran and
+    skipped trips, so the comparison is not between two runs of the full path; with them off, and (first grid) with TAU_H2_WPB=2
+    (the multi-wave kernels have no exits), it did not.  The child processes run one after another."""
     import subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     code = ("import sys; sys.path.insert(0, %r); import fluid_sims_amd as f, numpy as np\n"
-            "h = f.Hypersonic2D(%d, %d); h.init(); t = h.step(%d)\n"
-            "st = h.download(); np.savez(sys.argv[1], *st, t=np.float64(t if t is not None else 0.0))\n" % (root, W, H, steps))
+            "h = f.Hypersonic2D(%d, %d); h.init(); h.uniform_trips(True); t = h.step(%d); s, n, en = h.uniform_trips(False)\n"
+            "st = h.download(); np.savez(sys.argv[1], *st, t=np.float64(t if t is not None else 0.0), skipped=s, trips=n, enabled=en)\n"
+            % (root, W, H, steps))
     outs = []
-    for ex in ("1", "0"):
-        out = tmp_path / f"x{ex}.npz"
-        r = subprocess.run([sys.executable, "-c", code, str(out)], capture_output=True, text=True, env=dict(os.environ, TAUH2_UNIFORM_EXITS=ex))
+    runs = (("1", "1"), ("0", "1")) + ((("1", "2"),) if W == 2100 else ())   # (TAU_H2_WPB=2 on the first grid only)
+    for ex, wpb in runs:
+        out = tmp_path / f"x{ex}_{wpb}.npz"
+        r = subprocess.run([sys.executable, "-c", code, str(out)], capture_output=True, text=True,
+                           env=dict(os.environ, TAUH2_UNIFORM_EXITS=ex, TAU_H2_WPB=wpb))
         assert r.returncode == 0, r.stderr[-1500:]
         outs.append(np.load(out))
-    a, b = outs
-    assert float(a["t"]) == float(b["t"])
-    for k in ("arr_0", "arr_1", "arr_2", "arr_3"):
-        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), k
+    a, b, c = outs + [None] * (3 - len(outs))
+    for o in outs[1:]:
+        assert float(a["t"]) == float(o["t"])
+        for k in ("arr_0", "arr_1", "arr_2", "arr_3"):
+            assert np.array_equal(a[k].view(np.uint32), o[k].view(np.uint32)), k
     assert float(np.abs(a["arr_1"] - a["arr_1"][0, -1]).max()) > 1.0      # a shock layer exists: not two runs of pure free stream
+    sk, tr = int(a["skipped"]), int(a["trips"])
+    print((W, H), "step", steps, f"skipped trips {sk} of {tr} ({sk / max(tr, 1):.3f})")
+    assert bool(a["enabled"]) and 0 < sk < tr, "exits on: the kernel with the exits ran and skipped trips"
+    assert not bool(b["enabled"]) and int(b["skipped"]) == 0, "TAUH2_UNIFORM_EXITS=0: no exit"
+    if c is not None:
+        assert not bool(c["enabled"]) and int(c["skipped"]) == 0, "TAU_H2_WPB=2 runs a kernel without the exits"
